@@ -29,13 +29,16 @@ the full superset line LAST; a rank that catches an exception in a secondary leg
 every rank carries a watchdog that dumps its stacks and exits after MAPF_BENCH_WATCHDOG seconds (default 480, below the driver's 600).
 On one rank there is one line and a secondary-leg exception is reported as `dqn_error` beside the primary numbers.
 
-Timed region: the K steps behind the W warm-up steps of the tape.  One launch is ~21 us, so K = 20 would be a 0.5 ms
-sample: the K-step stretch is replayed R times back to back (one rewind launch of the agent positions between two
-repetitions, inside the timed region and charged to it) until the region is >= ~12 ms; `steps` stays K, `timed_repeats` = R,
-`ms_per_step` = elapsed / (K R).  `roofline.frac` is the BASELINE configuration's number (4096 environments: the 84 MB of navi
+Timed region: exactly the K steps behind the W warm-up steps of the tape, `ms_per_step` = elapsed / K.  One launch is ~21 us,
+so a K below a few hundred is a short sample: pick K from `ms_per_step`.  `roofline.frac` is the BASELINE configuration's number (4096 environments: the 84 MB of navi
 records + 80 MB of observations stay in the 256 MiB Infinity Cache between launches); `roofline.frac_out_of_cache` is the
 same kernel on 4x the environments (observation writes go to HBM, the per-step navi reads still fit the cache) and
 `roofline.frac_hbm_proper` on 8x (reads and writes both beyond the cache) -- see out_of_cache_leg.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step returned (VecEnvironment.step: obs, pos,
+reward, done, reward_class) as DIR/<name>.npy in float32, for a fixed, seeded sample of the environments that keeps the files
+under 64 MB (all of them at small --envs).  With the same arguments the scenarios and the action tape are the same from run to
+run, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -54,7 +57,8 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
-MIN_TIMED_S = 0.012   # the timed region is at least this long whatever --steps says (see the module docstring)
+DUMP_BYTES = 60 << 20  # --dump-outputs: budget of the written files (below the 64 MB bound)
+DUMP_SEED = 20240601   # --dump-outputs: seed of the environment sample
 MALL_BYTES = 256 << 20  # Infinity Cache
 
 
@@ -86,7 +90,29 @@ def parse_args(argv=None):
     ap.add_argument("--curriculum-iters", type=int, default=200, help="timed curriculum actor iterations")
     ap.add_argument("--ref-shape-updates", type=int, default=100, help="timed updates at the reference's training shape (and train-loop pairs)")
     ap.add_argument("--ref-shape-warmup", type=int, default=150, help="untimed updates in front of them (graph captures of the buckets the replay produces)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (a seeded sample of the environments) as DIR/<name>.npy, float32")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+def dump_outputs(out_dir, outs, E, N):
+    """The arrays the last timed VecEnvironment.step returned, on the host as float32: the same environments of every run (a seeded
+    sample in ascending order when all of them would exceed DUMP_BYTES)."""
+    import numpy as np
+    import torch
+
+    obs, pos, rew, done, rc = outs
+    per_env = 4 * (N * (obs[0, 0].numel() + 2 + 1 + 1) + 1)  # float32 bytes of one environment's obs, pos, reward, reward_class, done
+    n = min(E, max(1, DUMP_BYTES // per_env))
+    idx = np.arange(E) if n == E else np.sort(np.random.RandomState(DUMP_SEED).choice(E, n, replace=False))
+    sel = torch.from_numpy(idx.astype(np.int64)).to(obs.device)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in (("obs", obs), ("pos", pos), ("reward", rew), ("done", done), ("reward_class", rc)):
+        np.save(os.path.join(out_dir, name + ".npy"), t.index_select(0, sel).float().cpu().numpy())
+    log("bench.py: outputs of the last timed step (%d of %d environments) written to %s" % (n, E, out_dir))
 
 
 # --------------------------------------------------------------------------------------------------------
@@ -428,17 +454,11 @@ def main():
     # ---- untimed replays ----
     # (two untimed passes over the whole tape first: the recording pass above ran interleaved with the policy's own kernels, and a
     # profile of this command should be dominated by launches in the regime the timed region measures)
-    e_a, e_b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     for rep in range(2):
         env.set_agents(agents_dev)
-        if rep:
-            e_a.record()
         for t in range(T):
             env.step(tape[t])
-    e_b.record()
     torch.cuda.synchronize()
-    est_step_s = max(e_a.elapsed_time(e_b) * 1e-3 / T, 1e-6)
-    R = int(min(2000, max(1, -(-MIN_TIMED_S // (K * est_step_s)))))  # repetitions of the K-step stretch: timed region >= ~12 ms
 
     # ---- CPU baseline (rank 0) BEFORE the process group exists: the other ranks then sleep in the rendezvous instead of
     # spinning on their GPUs / holding host cores while the oracle processes are being timed ----
@@ -465,9 +485,6 @@ def main():
         else:
             dist.init_process_group(args.dist_backend, timeout=tmo)
         assert dist.get_world_size() == world
-        rr = torch.tensor([R], dtype=torch.int64, device=dev)
-        dist.all_reduce(rr, op=dist.ReduceOp.MAX)  # same amount of timed work on every rank
-        R = int(rr.item())
         # who is here: (rank, HIP device index, PCI bus id) of every rank, gathered once
         me = torch.zeros((world, 3), dtype=torch.int64, device=dev)
         try:
@@ -482,20 +499,16 @@ def main():
     env.set_agents(agents_dev)
     for t in range(W):
         env.step(tape[t])
-    pos_w = env.agents_pos()  # state behind the warm-up steps: the rewind target of repetitions 2..R
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(R)]
+    ev_a, ev_b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     t_start = time.perf_counter()
-    for r in range(R):
-        if r:
-            env.set_agents(pos_w, sync=False)  # one small launch, inside the timed region
-        evs[r][0].record()  # HIP events on the launch stream around each K-launch stretch (no per-launch event traffic)
-        for k in range(K):
-            env.step(tape[W + k])
-        evs[r][1].record()
+    ev_a.record()  # HIP events on the launch stream around the K launches (no per-launch event traffic)
+    for k in range(K):
+        last = env.step(tape[W + k])
+    ev_b.record()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -503,13 +516,15 @@ def main():
     elapsed = time.perf_counter() - t_start
     env.check_status()
     assert torch.equal(env.pos, final_pos_first_pass), "replay diverged from the recording pass"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, E, N)
 
     if world > 1:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
 
-    kern_avg_s = sum(a.elapsed_time(b) for a, b in evs) * 1e-3 / (K * R)  # mean launch-to-launch duration of env_step_kernel (incl. the ~1 us boundary)
+    kern_avg_s = ev_a.elapsed_time(ev_b) * 1e-3 / K  # mean launch-to-launch duration of env_step_kernel (incl. the ~1 us boundary)
     alg_bytes_per_env = L * L + 821 * N + 1  # fused step+observe, one byte per flag/cell
     alg_bytes = alg_bytes_per_env * E
     achieved = alg_bytes / kern_avg_s / 1e9
@@ -517,13 +532,12 @@ def main():
     backend = "none" if world == 1 else ("%s, dist.get_world_size()=%d" % (dist.get_backend(), dist.get_world_size()))
     result = {
         "metric": "env_steps_per_sec",
-        "value": world * E * K * R / elapsed,
+        "value": world * E * K / elapsed,
         "unit": "env-steps/s",
         "n_gpus": world,
         "steps": K,
         "warmup": W,
-        "ms_per_step": elapsed / (K * R) * 1e3,
-        "timed_repeats": R,
+        "ms_per_step": elapsed / K * 1e3,
         "timed_region_ms": elapsed * 1e3,
         "higher_is_better": True,
         "scaling": "weak",

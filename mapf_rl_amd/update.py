@@ -19,7 +19,6 @@ head, the loss, gradient accumulation, the clip, Adam, weight re-packing and the
 
 Parameters, gradients and Adam moments live in flat fp32 buffers (`FlatParams`): the module's parameters are views of them, so
 `state_dict()` / `load_state_dict()` / checkpoints are unaffected, and the data-parallel all-reduce is one collective over one buffer."""
-import contextlib
 import ctypes
 import os
 
@@ -687,34 +686,26 @@ class FusedUpdate:
         hin0, _, hr, _, ctxs, info, _, _ = saves
         hrf = hr.view(2 * R, 256)
         rows_k = WGRAD_SPLIT if compact else 8192
-        # the recurrence's weight / bias gradients (five tall GEMMs + their sums: ~0.3 ms of small launches at few agents) depend only
-        # on what the BPTT kernel wrote, the encoder's backward chain below only on d_gi1: inside a capture they become two branches
-        # of the graph (a second stream that forks here and joins before the optimizer step).  Everything the branch reads is held by
-        # `c` / `outs_b` until the join; what it allocates, it allocates on its own stream.
-        # Eagerly too (config 2: nine ~50 us launches that would otherwise sit between the BPTT kernel and the encoder's backward).
-        # Several ranks: the recurrence's and the head's piece of the gradient exchange is issued FROM the branch, behind the last
-        # gradient it contains (the collective is ordered behind the stream it is issued on), so it travels while the encoder's
-        # backward chain runs on the main stream.  (Rounds 3-4 kept one stream with several ranks and lost the overlap.)
+        # Every gradient is computed on this one stream.  (The recurrence's weight / bias gradients used to run on the learner's second
+        # stream beside the encoder's backward chain; the update's parameters then differed in the last bits from those of the same
+        # update computed on one stream, and the backward graph captured with that fork made hipGraphLaunch segfault on its replay.)
+        # Several ranks: the recurrence's and the head's piece of the gradient exchange (12 % of the bytes) is issued as soon as those
+        # gradients are final; the collective runs on its own stream behind this point, so it travels while the encoder's backward
+        # chain runs here.
         from .learner import exchanging
 
         ex = exchanging()
-        aux = self.lr._side if (self._capturing or self.lr.grad_hook is None) else None
-        cur_s = torch.cuda.current_stream(dev)
         n_all, split = flat.grads.numel(), lr.bucket.split
         # (inside a capture no collective is issued: the captured stage ends where the gradients are final, see _run_graphed)
-        two_pieces = ex and not self._capturing and aux is not None and split is not None and 0 < split < n_all
-        if aux is not None:
-            aux.wait_stream(cur_s)
-        with (torch.cuda.stream(aux) if aux is not None else contextlib.nullcontext()):
-            st_x = _stream(dev)
-            _tall_tn_into(flat.mem(G, "recurrent.weight_hh"), d_gh1, hin0, rows_k)
-            _tall_tn_into(flat.span(G, "comm.self_attn.W_Q.weight", "comm.self_attn.W_V.weight"), d_qkv.view(2 * R, 384), hrf, rows_k)
-            _tall_tn_into(flat.mem(G, "comm.self_attn.W_O.weight"), d_info.view(2 * R, 64), ctxs.view(2 * R, 128), rows_k)
-            _tall_tn_into(flat.mem(G, "comm.update_cell.weight_ih"), d_gi2.view(2 * R, 768), info.view(2 * R, 64), rows_k)
-            _tall_tn_into(flat.mem(G, "comm.update_cell.weight_hh"), d_gh2.view(2 * R, 768), hrf, rows_k)
-            bias_names = ("recurrent.bias_ih", "recurrent.bias_hh", "comm.self_attn.W_Q.bias", "comm.self_attn.W_K.bias", "comm.self_attn.W_V.bias",
-                          "comm.update_cell.bias_ih", "comm.update_cell.bias_hh")
-            check(lib.mapf_recurrent_bias_grads(_ptr(bsum), E_, _ptr_array([flat.mem(G, k) for k in bias_names]), st_x), "mapf_recurrent_bias_grads")
+        two_pieces = ex and not self._capturing and split is not None and 0 < split < n_all
+        _tall_tn_into(flat.mem(G, "recurrent.weight_hh"), d_gh1, hin0, rows_k)
+        _tall_tn_into(flat.span(G, "comm.self_attn.W_Q.weight", "comm.self_attn.W_V.weight"), d_qkv.view(2 * R, 384), hrf, rows_k)
+        _tall_tn_into(flat.mem(G, "comm.self_attn.W_O.weight"), d_info.view(2 * R, 64), ctxs.view(2 * R, 128), rows_k)
+        _tall_tn_into(flat.mem(G, "comm.update_cell.weight_ih"), d_gi2.view(2 * R, 768), info.view(2 * R, 64), rows_k)
+        _tall_tn_into(flat.mem(G, "comm.update_cell.weight_hh"), d_gh2.view(2 * R, 768), hrf, rows_k)
+        bias_names = ("recurrent.bias_ih", "recurrent.bias_hh", "comm.self_attn.W_Q.bias", "comm.self_attn.W_K.bias", "comm.self_attn.W_V.bias",
+                      "comm.update_cell.bias_ih", "comm.update_cell.bias_hh")
+        check(lib.mapf_recurrent_bias_grads(_ptr(bsum), E_, _ptr_array([flat.mem(G, k) for k in bias_names]), st), "mapf_recurrent_bias_grads")
         # ---- input projection ----
         if compact:
             d_gi_rows = d_gi1[:M]
@@ -728,20 +719,12 @@ class FusedUpdate:
             check(lib.mapf_dedup_sum(To, B, Nc, M, 1536, _ptr(po.gidx), _ptr(po.umap), _ptr(po.row_tbp), _ptr(d_gi_rows), _ptr(d_gi_u), st),
                   "mapf_dedup_sum")
             d_gi_rows = d_gi_u
-        if aux is not None:  # (the input projection's weight gradient joins the side branch: only the encoder's chain needs g_lat)
-            aux.wait_stream(cur_s)
-            with torch.cuda.stream(aux):
-                _tall_tn_into(flat.mem(G, "recurrent.weight_ih"), d_gi_rows, c.lat, rows=4096)
-                # the recurrence's and the head's gradients are final on this branch: their piece of the exchange (12 % of the bytes)
-                if two_pieces:
-                    lr.bucket.begin(split, n_all)
+        _tall_tn_into(flat.mem(G, "recurrent.weight_ih"), d_gi_rows, c.lat, rows=4096)
+        if two_pieces:  # the recurrence's and the head's gradients are final: their piece of the exchange
+            lr.bucket.begin(split, n_all)
         g_lat = latent_grad_rows(d_gi_rows, self._on_w_iht)
-        if aux is None:
-            _tall_tn_into(flat.mem(G, "recurrent.weight_ih"), d_gi_rows, c.lat, rows=4096)
         # ---- encoder: backward-data chain in one kernel, then the weight-gradient kernels ----
-        self._encoder_backward(po.obs_rows, Mu, c.acts, c.lat, c.bits, g_lat, c.wpt, aux, getattr(c, "valid_rows", None))
-        if aux is not None:
-            cur_s.wait_stream(aux)
+        self._encoder_backward(po.obs_rows, Mu, c.acts, c.lat, c.bits, g_lat, c.wpt, getattr(c, "valid_rows", None))
         if ex and self._capturing:
             return None  # several ranks, captured: the exchange and the optimizer step follow the graph (_run_graphed)
         # ---- the exchange (its second piece: the encoder's gradients), clip, Adam ----
@@ -1074,9 +1057,8 @@ class FusedUpdate:
 
     WGRAD_MERGED = os.environ.get("MAPF_WGRAD_MERGED", "1") != "0"  # (the variable: A/B runs)
 
-    def _encoder_backward(self, obs_rows, M, acts, lat, bits, g_lat, wpt, aux=None, valid=None):
-        """aux: a second stream for what only needs the backward-data kernel's outputs besides the six 3x3 weight-gradient launches
-        (bias sums, conv0's and the 1x1 head's weight gradients: ~0.15 ms of small launches at few agents); the caller joins it."""
+    def _encoder_backward(self, obs_rows, M, acts, lat, bits, g_lat, wpt, valid=None):
+        """The encoder's backward-data chain, then its weight and bias gradients (all on the current stream)."""
         dev, flat = self.dev, self.flat
         G, st, bf = flat.grads, _stream(dev), torch.bfloat16
         nblk = -(-M // ENC_OBS_PER_BLOCK)
@@ -1096,22 +1078,18 @@ class FusedUpdate:
                                             _ptr(scale), st), "mapf_encoder_backward")
         names = ["obs_encoder.0", "obs_encoder.2.block1", "obs_encoder.2.block2", "obs_encoder.3.block1", "obs_encoder.3.block2",
                  "obs_encoder.4.block1", "obs_encoder.4.block2", "obs_encoder.5"]
-        if aux is not None:
-            aux.wait_stream(torch.cuda.current_stream(dev))
-        with (torch.cuda.stream(aux) if aux is not None else contextlib.nullcontext()):
-            st_x = _stream(dev)
-            ws0 = torch.empty((ENC_WGRAD0_PARTS, 128, 64), dtype=torch.float32, device=dev)
-            if valid is not None:
-                check(lib.mapf_encoder_wgrad0_bounded(_ptr(gz[0]), _ptr(obs_rows), 1, M, _ptr(valid), _ptr(scale), _ptr(ws0), st_x), "mapf_encoder_wgrad0_bounded")
-            else:
-                check(lib.mapf_encoder_wgrad0(_ptr(gz[0]), _ptr(obs_rows), 1, M, _ptr(scale), _ptr(ws0), st_x), "mapf_encoder_wgrad0")
-            # bias gradients from the backward kernel's per-workgroup partials, conv0's weight gradient from its slabs (columns
-            # j = ci*9 + ky*3 + kx -> the weight's memory [co][ky][kx][ci]): two small launches of this library
-            check(lib.mapf_encoder_small_grads(_ptr(gb_part), nblk, _ptr(flat.span(G, names[0] + ".bias", names[6] + ".bias")), _ptr(gb7_part), 4 * nblk,
-                                               _ptr(flat.mem(G, names[7] + ".bias")), _ptr(ws0), ENC_WGRAD0_PARTS, _ptr(flat.mem(G, names[0] + ".weight")),
-                                               _ptr(torch.empty(65536, dtype=torch.float32, device=dev)), st_x), "mapf_encoder_small_grads")
-            # the 1x1 head: [16, 128] = gz7^T acts6 over M * 49 positions (f16, the chain's loss scale taken out in fp32)
-            tall_tn_into(flat.mem(G, names[7] + ".weight").view(16, 128), gz7, acts[6].reshape(M * 49, 128), scale=scale)
+        ws0 = torch.empty((ENC_WGRAD0_PARTS, 128, 64), dtype=torch.float32, device=dev)
+        if valid is not None:
+            check(lib.mapf_encoder_wgrad0_bounded(_ptr(gz[0]), _ptr(obs_rows), 1, M, _ptr(valid), _ptr(scale), _ptr(ws0), st), "mapf_encoder_wgrad0_bounded")
+        else:
+            check(lib.mapf_encoder_wgrad0(_ptr(gz[0]), _ptr(obs_rows), 1, M, _ptr(scale), _ptr(ws0), st), "mapf_encoder_wgrad0")
+        # bias gradients from the backward kernel's per-workgroup partials, conv0's weight gradient from its slabs (columns
+        # j = ci*9 + ky*3 + kx -> the weight's memory [co][ky][kx][ci]): two small launches of this library
+        check(lib.mapf_encoder_small_grads(_ptr(gb_part), nblk, _ptr(flat.span(G, names[0] + ".bias", names[6] + ".bias")), _ptr(gb7_part), 4 * nblk,
+                                           _ptr(flat.mem(G, names[7] + ".bias")), _ptr(ws0), ENC_WGRAD0_PARTS, _ptr(flat.mem(G, names[0] + ".weight")),
+                                           _ptr(torch.empty(65536, dtype=torch.float32, device=dev)), st), "mapf_encoder_small_grads")
+        # the 1x1 head: [16, 128] = gz7^T acts6 over M * 49 positions (f16, the chain's loss scale taken out in fp32)
+        tall_tn_into(flat.mem(G, names[7] + ".weight").view(16, 128), gz7, acts[6].reshape(M * 49, 128), scale=scale)
         if (self.WGRAD_MERGED or valid is not None) and gz.stride(0) == acts.stride(0) == M * 6272:
             # the six 3x3 layers' weight gradients in ONE launch (one workgroup per CU: 6 x 21 partitions x 2 slabs) and one sum -- six
             # serial (wgrad 54-75 us, sum 12-17 us) pairs were the last 400 us of a 6-agent update's chain
