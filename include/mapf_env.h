@@ -4,7 +4,7 @@
  * This is the drop-in boundary for the reference's environment hot path (ZiyuanMa/MAPF_RL):
  * the reference has no FFI, the path sits behind the Python class `Environment`
  * (reference environment.py:74-467).  Each entry point names the reference code it replaces.
- * A handle owns E independent lock-step environments of identical shape (L x L map, N agents,
+ * A handle owns E independent lock-step environments of identical shape (L x L map, L 2..128, N agents,
  * FOV radius r) resident in HBM; all heavy entry points are asynchronous launches on the
  * caller's HIP stream.
  *
@@ -40,7 +40,7 @@ extern "C" {
 #define MAPF_ERR_ACTION (-2)        /* AssertionError 'action index out of range', environment.py:289-290 */
 #define MAPF_ERR_OVERLAP (-3)       /* RuntimeError('unique'): two agents on one cell, environment.py:424-428 */
 #define MAPF_ERR_HIP (-4)           /* a HIP runtime call failed (no GPU, OOM, launch failure) */
-#define MAPF_ERR_UNSUPPORTED (-5)   /* shape outside what the kernels are built for (L > 64, N > 255, r != 4) */
+#define MAPF_ERR_UNSUPPORTED (-5)   /* shape outside what the kernels are built for (L > 64 -- L > 128 for mapf_create_large --, N > 255, r != 4) */
 #define MAPF_ERR_NO_SPACE (-6)      /* ValueError from placement exhaustion, environment.py:120 */
 #define MAPF_ERR_NOT_READY (-7)     /* step/observe before load + build_navi */
 
@@ -65,6 +65,14 @@ int mapf_device_count(void);
  * obs_shape (6,9,9) is hard-wired, config.py:14, model.py:148,164,235).
  */
 int mapf_create(int num_envs, int map_len, int num_agents, int obs_radius, int device, mapf_env_t **out);
+
+/*
+ * The same for maps of side 65..128 (environment.py:75-76: the reference has no cap on map_length): N 1..255, r == 4;
+ * MAPF_ERR_UNSUPPORTED for a map side outside 65..128 (mapf_create covers 2..64: the two never overlap).  Every other entry point
+ * takes the handle with the same semantics, layouts and error reporting, except mapf_multi_create (MAPF_ERR_UNSUPPORTED: step such
+ * a handle on its own).  Its kernels hold a map row as two 64-bit words.
+ */
+int mapf_create_large(int num_envs, int map_len, int num_agents, int obs_radius, int device, mapf_env_t **out);
 int mapf_destroy(mapf_env_t *env);
 
 /* config.reward_fn (config.py:8-12) in MAPF_RC_* order; default {-0.075, 0, -0.075, -0.5, 3}. */
@@ -148,7 +156,8 @@ int mapf_observe_masked(mapf_env_t *env, const uint8_t *mask_dev, uint8_t *obs_d
  * agents) together with the buffers their step reads and writes -- per handle i the arguments of mapf_step (actions, obs, obs_bits,
  * pos, reward_class, reward, done) and the u8 [E_i] mask of mapf_observe_masked / mapf_reset_envs (the actor's end-of-episode flags).
  * All pointers are device pointers that must stay valid while the set lives; the arrays of pointers themselves are host arrays read
- * at creation.  MAPF_ERR_UNSUPPORTED for a shape outside the limits (callers then step the handles one by one).
+ * at creation.  MAPF_ERR_UNSUPPORTED for a shape outside the limits or a handle of mapf_create_large (callers then step the handles
+ * one by one).
  *   mapf_multi_step             = mapf_step of every handle, ONE launch (same outputs, bit for bit);
  *   mapf_multi_reset            = mapf_reset_envs(mask_i, seed = reset_seeds[i] + *tick_dev) of every handle, ONE launch
  *                                 (reset_seeds: host array given at creation, NULL = i * a constant; tick_dev: uint64 in device

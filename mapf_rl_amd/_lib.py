@@ -18,6 +18,7 @@ SYMBOLS = [
     ("mapf_strerror", ctypes.c_char_p, [_i]),
     ("mapf_device_count", _i, []),
     ("mapf_create", _i, [_i, _i, _i, _i, _i, ctypes.POINTER(_vp)]),
+    ("mapf_create_large", _i, [_i, _i, _i, _i, _i, ctypes.POINTER(_vp)]),
     ("mapf_destroy", _i, [_vp]),
     ("mapf_set_reward_table", _i, [_vp, ctypes.POINTER(_f)]),
     ("mapf_load", _i, [_vp, _vp, _vp, _vp, _i, _vp]),

@@ -4,7 +4,8 @@
 // step / observe, reference environment.py:198-467.  See include/mapf_env.h for the boundary and
 // DESIGN.md for the data layout and the per-kernel roofline.
 //
-// Data layout in HBM (per handle; W = uint32_t when L <= 32, uint64_t when L <= 64):
+// Data layout in HBM (per handle; W = uint32_t when L <= 32, uint64_t when L <= 64; maps of side 65..128 -- mapf_create_large -- run
+// the kernels of mapf_env_large.hip, with a row of two uint64_t words and 64-byte navi records, layout in mapf_env_large.h):
 //   map_rows W[E][L]          bit y of row x = obstacle at (x, y)
 //   agents   int16[E][N][2]   current (row, col)
 //   goals    int16[E][N][2]
@@ -41,6 +42,7 @@
 #include <vector>
 
 #include "mapf_env.h"
+#include "mapf_env_large.h"
 
 namespace {
 
@@ -647,6 +649,7 @@ __global__ void unpack_navi_kernel(long long fields, int L, const NaviRec<W> *na
 struct mapf_env {
     int E, L, N, R, device;
     bool wide;  // 64-bit rows
+    bool large;  // L > 64: 128-bit rows, kernels of mapf_env_large.hip
     void *map_rows;
     int16_t *agents;
     int16_t *goals;
@@ -684,7 +687,7 @@ namespace {
         }                                                                                               \
     } while (0)
 
-size_t word_bytes(const mapf_env *h) { return h->wide ? 8 : 4; }
+size_t word_bytes(const mapf_env *h) { return h->large ? mapf_large::kRowBytes : (h->wide ? 8 : 4); }
 
 struct DeviceGuard {
     int prev = -1;
@@ -890,6 +893,33 @@ StepParams make_params(mapf_env *h) {
 
 inline unsigned blocks_for(long long n, int threads) { return (unsigned)((n + threads - 1) / threads); }
 
+// step / observe of a large handle (mapf_env_large.hip): actions == nullptr observes only
+int large_step(mapf_env *h, const int8_t *actions, const uint8_t *mask, uint8_t *obs, uint32_t *obs_bits, int16_t *pos, int8_t *rclass,
+               float *reward, uint8_t *done, void *stream) {
+    mapf_large::StepArgs a{};
+    a.E = h->E;
+    a.L = h->L;
+    a.N = h->N;
+    a.map_rows = h->map_rows;
+    a.agents = h->agents;
+    a.goals = h->goals;
+    a.navi = h->navi;
+    a.steps = h->steps;
+    a.status = h->status;
+    a.actions = actions;
+    a.obs = obs;
+    a.obs_bits = obs_bits;
+    a.obs_bits_rd = ((h->N * 486 + 31) / 32 + 3) & ~3;
+    a.pos_out = pos;
+    a.rclass = rclass;
+    a.reward = reward;
+    a.done = done;
+    a.mask = mask;
+    std::memcpy(a.rtab, h->rtab, sizeof(a.rtab));
+    HIP_TRY(mapf_large::step(a, static_cast<hipStream_t>(stream)));
+    return MAPF_OK;
+}
+
 // ---- host scenario generator (Rng, generate_one, generate_scenarios): host-only C++ kept in its own file so that the CPU
 // sanitizer target (tests/test_sanitize_cpu.py) compiles exactly these lines with g++ -fsanitize=address,undefined ----
 #include "mapf_generate_host.inc"
@@ -920,11 +950,11 @@ int mapf_device_count(void) {
     return n;
 }
 
-int mapf_create(int num_envs, int map_len, int num_agents, int obs_radius, int device, mapf_env_t **out) {
-    if (!out) return MAPF_ERR_INVALID_ARG;
-    *out = nullptr;
-    if (num_envs < 1 || map_len < 2 || num_agents < 1 || device < 0) return MAPF_ERR_INVALID_ARG;
-    if (map_len > 64 || num_agents > 255 || obs_radius != 4) return MAPF_ERR_UNSUPPORTED;
+}  // extern "C"
+
+namespace {
+// the handle of mapf_create / mapf_create_large, arguments already checked
+int create_handle(int num_envs, int map_len, int num_agents, int obs_radius, int device, mapf_env_t **out) {
     if (device >= mapf_device_count()) return MAPF_ERR_HIP;
     mapf_env *h = new (std::nothrow) mapf_env();
     if (!h) return MAPF_ERR_HIP;
@@ -934,6 +964,7 @@ int mapf_create(int num_envs, int map_len, int num_agents, int obs_radius, int d
     h->R = obs_radius;
     h->device = device;
     h->wide = map_len > 32;
+    h->large = map_len > 64;
     h->loaded = h->navi_ready = false;
     h->dbg = nullptr;
     const char *tv = std::getenv("MAPF_STEP_THREADS");
@@ -977,6 +1008,25 @@ int mapf_create(int num_envs, int map_len, int num_agents, int obs_radius, int d
     }
     *out = h;
     return MAPF_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int mapf_create(int num_envs, int map_len, int num_agents, int obs_radius, int device, mapf_env_t **out) {
+    if (!out) return MAPF_ERR_INVALID_ARG;
+    *out = nullptr;
+    if (num_envs < 1 || map_len < 2 || num_agents < 1 || device < 0) return MAPF_ERR_INVALID_ARG;
+    if (map_len > 64 || num_agents > 255 || obs_radius != 4) return MAPF_ERR_UNSUPPORTED;
+    return create_handle(num_envs, map_len, num_agents, obs_radius, device, out);
+}
+
+int mapf_create_large(int num_envs, int map_len, int num_agents, int obs_radius, int device, mapf_env_t **out) {
+    if (!out) return MAPF_ERR_INVALID_ARG;
+    *out = nullptr;
+    if (num_envs < 1 || map_len < 2 || num_agents < 1 || device < 0) return MAPF_ERR_INVALID_ARG;
+    if (map_len < mapf_large::kMinLen || map_len > mapf_large::kMaxLen || num_agents > 255 || obs_radius != 4) return MAPF_ERR_UNSUPPORTED;
+    return create_handle(num_envs, map_len, num_agents, obs_radius, device, out);
 }
 
 int mapf_destroy(mapf_env_t *h) {
@@ -1028,7 +1078,9 @@ int mapf_load(mapf_env_t *h, const int8_t *maps, const int16_t *agents, const in
         hipLaunchKernelGGL(check_positions_kernel, dim3(blocks_for(E * N * 2, 256)), dim3(256), 0, s,
                            (long long)(E * N * 2), h->L, h->agents, h->goals, h->status);
     }
-    if (h->wide)
+    if (h->large)
+        HIP_TRY(mapf_large::pack_maps(h->E, h->L, maps_dev, h->map_rows, s));
+    else if (h->wide)
         hipLaunchKernelGGL(pack_map_kernel<uint64_t>, dim3(blocks_for(E * L, 256)), dim3(256), 0, s, h->E, h->L,
                            maps_dev, static_cast<uint64_t *>(h->map_rows));
     else
@@ -1065,7 +1117,10 @@ int mapf_load_envs(mapf_env_t *h, const int32_t *env_ids, int n, const int8_t *m
     HIP_TRY(hipMemcpyAsync(d_ag, agents, (size_t)n * N * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d_go, goals, (size_t)n * N * 4, hipMemcpyHostToDevice, s));
     const long long slots = (long long)n * h->N;
-    if (h->wide) {
+    if (h->large) {
+        HIP_TRY(mapf_large::scatter_load(n, h->L, h->N, d_ids, d_maps, d_ag, d_go, h->map_rows, h->agents, h->goals, h->steps, h->E, h->status, s));
+        HIP_TRY(mapf_large::build_navi(n, h->E, h->L, h->N, h->map_rows, h->goals, h->navi, h->status, d_ids, nullptr, s));
+    } else if (h->wide) {
         hipLaunchKernelGGL(scatter_load_kernel<uint64_t>, dim3(n), dim3(128), 0, s, n, h->L, h->N, d_ids, d_maps, d_ag, d_go,
                            static_cast<uint64_t *>(h->map_rows), h->agents, h->goals, h->steps, h->E, h->status);
         hipLaunchKernelGGL(navi_bfs_kernel<uint64_t>, dim3(blocks_for(slots * 64, 256)), dim3(256), 0, s, n, h->L, h->N,
@@ -1125,7 +1180,10 @@ int mapf_stage_next(mapf_env_t *h, float density, uint64_t seed, void *stream) {
     h->st_seed = seed;
     h->st_density = density;
     const long long fields = (long long)h->E * h->N;
-    if (h->wide) {
+    if (h->large) {
+        HIP_TRY(mapf_large::stage_fill(h->E, h->L, h->N, density, seed, h->st_map_rows, h->st_agents, h->st_goals, h->st_navi, h->epochs, h->status,
+                                       h->st_epoch, h->st_need, s));
+    } else if (h->wide) {
         hipLaunchKernelGGL(stage_fill_kernel<uint64_t>, dim3(h->E), dim3(64), 0, s, h->E, h->L, h->N, density, seed, static_cast<uint64_t *>(h->st_map_rows),
                            h->st_agents, h->st_goals, h->epochs, h->status, h->st_epoch, h->st_need);
         hipLaunchKernelGGL(navi_bfs_kernel<uint64_t>, dim3(blocks_for(fields * 64, 256)), dim3(256), 0, s, h->E, h->L, h->N,
@@ -1149,7 +1207,10 @@ int mapf_reset_envs(mapf_env_t *h, const uint8_t *mask_dev, float density, uint6
     if (h->staged && h->st_seed == seed && h->st_density == density) {
         // the flagged environments take over the scenario mapf_stage_next drew for their next epoch: one copy launch where the direct
         // path below draws, places and floods N fields (~0.1 ms on the actor's critical path whenever an episode ended)
-        if (h->wide)
+        if (h->large)
+            HIP_TRY(mapf_large::stage_swap(h->E, h->L, h->N, mask_dev, h->map_rows, h->agents, h->goals, h->navi, h->steps, h->epochs, h->status,
+                                           h->st_map_rows, h->st_agents, h->st_goals, h->st_navi, h->st_epoch, s));
+        else if (h->wide)
             hipLaunchKernelGGL(stage_swap_kernel<uint64_t>, dim3(h->E), dim3(256), 0, s, h->E, h->L, h->N, mask_dev, static_cast<uint64_t *>(h->map_rows),
                                h->agents, h->goals, static_cast<NaviRec<uint64_t> *>(h->navi), h->steps, h->epochs, h->status,
                                static_cast<const uint64_t *>(h->st_map_rows), h->st_agents, h->st_goals,
@@ -1160,6 +1221,12 @@ int mapf_reset_envs(mapf_env_t *h, const uint8_t *mask_dev, float density, uint6
                                static_cast<const uint32_t *>(h->st_map_rows), h->st_agents, h->st_goals,
                                static_cast<const NaviRec<uint32_t> *>(h->st_navi), h->st_epoch);
         HIP_TRY(hipGetLastError());
+        if (!mask_dev) h->loaded = h->navi_ready = true;
+        return MAPF_OK;
+    }
+    if (h->large) {
+        HIP_TRY(mapf_large::reset(h->E, h->L, h->N, mask_dev, density, seed, h->map_rows, h->agents, h->goals, h->navi, h->steps, h->epochs,
+                                  h->status, s));
         if (!mask_dev) h->loaded = h->navi_ready = true;
         return MAPF_OK;
     }
@@ -1205,7 +1272,9 @@ int mapf_build_navi(mapf_env_t *h, void *stream) {
     DeviceGuard guard(h->device);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const long long fields = (long long)h->E * h->N;
-    if (h->wide) {
+    if (h->large) {
+        HIP_TRY(mapf_large::build_navi(h->E, h->E, h->L, h->N, h->map_rows, h->goals, h->navi, h->status, nullptr, nullptr, s));
+    } else if (h->wide) {
         const long long waves = fields;
         hipLaunchKernelGGL(navi_bfs_kernel<uint64_t>, dim3(blocks_for(waves * 64, 256)), dim3(256), 0, s, h->E, h->L,
                            h->N, static_cast<const uint64_t *>(h->map_rows), h->goals,
@@ -1230,6 +1299,7 @@ int mapf_step(mapf_env_t *h, const int8_t *actions_dev, uint8_t *obs_dev, uint32
     if (!h || !actions_dev) return MAPF_ERR_INVALID_ARG;
     if (!h->loaded || ((obs_dev || obs_bits_dev) && !h->navi_ready)) return MAPF_ERR_NOT_READY;
     DeviceGuard guard(h->device);
+    if (h->large) return large_step(h, actions_dev, nullptr, obs_dev, obs_bits_dev, pos_dev, reward_class_dev, reward_dev, done_dev, stream);
     StepParams p = make_params(h);
     p.actions = actions_dev;
     p.obs = obs_dev;
@@ -1246,6 +1316,7 @@ int mapf_observe(mapf_env_t *h, uint8_t *obs_dev, uint32_t *obs_bits_dev, int16_
     if (!h || (!obs_dev && !obs_bits_dev)) return MAPF_ERR_INVALID_ARG;
     if (!h->loaded || !h->navi_ready) return MAPF_ERR_NOT_READY;
     DeviceGuard guard(h->device);
+    if (h->large) return large_step(h, nullptr, nullptr, obs_dev, obs_bits_dev, pos_dev, nullptr, nullptr, nullptr, stream);
     StepParams p = make_params(h);
     p.obs = obs_dev;
     p.obs_bits = obs_bits_dev;
@@ -1258,6 +1329,7 @@ int mapf_observe_masked(mapf_env_t *h, const uint8_t *mask_dev, uint8_t *obs_dev
     if (!h || (!obs_dev && !obs_bits_dev)) return MAPF_ERR_INVALID_ARG;
     if (!h->loaded || !h->navi_ready) return MAPF_ERR_NOT_READY;
     DeviceGuard guard(h->device);
+    if (h->large) return large_step(h, nullptr, mask_dev, obs_dev, obs_bits_dev, pos_dev, nullptr, nullptr, nullptr, stream);
     StepParams p = make_params(h);
     p.mask = mask_dev;
     p.obs = obs_dev;
@@ -1321,6 +1393,10 @@ int mapf_multi_create(int n, mapf_env_t *const *envs, const int8_t *const *actio
         if (!h || !actions_dev[i] || (!obs_dev[i] && !obs_bits_dev[i]) || h->device != m->device) {
             delete m;
             return MAPF_ERR_INVALID_ARG;
+        }
+        if (h->large) {  // (no merged launch for maps of side > 64: the caller steps such a handle on its own)
+            delete m;
+            return MAPF_ERR_UNSUPPORTED;
         }
         if (!h->loaded || !h->navi_ready) {
             delete m;
@@ -1433,7 +1509,9 @@ int mapf_get_navi(mapf_env_t *h, uint8_t *navi_dev, void *stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     const long long fields = (long long)h->E * h->N;
     const long long total = fields * 4 * h->L * h->L;
-    if (h->wide)
+    if (h->large)
+        HIP_TRY(mapf_large::unpack_navi(fields, h->L, h->navi, navi_dev, s));
+    else if (h->wide)
         hipLaunchKernelGGL(unpack_navi_kernel<uint64_t>, dim3(blocks_for(total, 256)), dim3(256), 0, s, fields, h->L,
                            static_cast<const NaviRec<uint64_t> *>(h->navi), navi_dev);
     else
@@ -1465,7 +1543,9 @@ int mapf_get_maps(mapf_env_t *h, int8_t *maps_dev, void *stream) {
     DeviceGuard guard(h->device);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const long long total = (long long)h->E * h->L * h->L;
-    if (h->wide)
+    if (h->large)
+        HIP_TRY(mapf_large::unpack_maps(h->E, h->L, h->map_rows, maps_dev, s));
+    else if (h->wide)
         hipLaunchKernelGGL(unpack_map_kernel<uint64_t>, dim3(blocks_for(total, 256)), dim3(256), 0, s, h->E, h->L,
                            static_cast<const uint64_t *>(h->map_rows), maps_dev);
     else

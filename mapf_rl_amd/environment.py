@@ -65,8 +65,14 @@ class VecEnvironment:
         self._h = ctypes.c_void_p()
         dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
         self.device = torch.device("cuda", dev_index)
-        check(lib.mapf_create(num_envs, map_length, num_agents, obs_radius, dev_index, ctypes.byref(self._h)),
-              "mapf_create")
+        if map_length > 128:
+            raise ValueError("map_length %d: the environment supports map sides up to 128" % map_length)
+        if map_length > 64:  # two 64-bit words per map row (mapf_create_large)
+            check(lib.mapf_create_large(num_envs, map_length, num_agents, obs_radius, dev_index, ctypes.byref(self._h)),
+                  "mapf_create_large")
+        else:
+            check(lib.mapf_create(num_envs, map_length, num_agents, obs_radius, dev_index, ctypes.byref(self._h)),
+                  "mapf_create")
         self.reward_fn = dict(DEFAULT_REWARD_FN if reward_fn is None else reward_fn)
         tab = (ctypes.c_float * 5)(*[float(self.reward_fn[k]) for k in REWARD_KEYS])
         check(lib.mapf_set_reward_table(self._h, tab), "mapf_set_reward_table")

@@ -61,23 +61,29 @@ def create_test(agent_range, map_range, test_num=TEST_NUM, density=-1.0, seed=1,
                 time_limit=5.0):
     """reference test.py:23-79: writes ./test{agents}_{map}.pkl.  with_opt_steps=True labels every scenario with the
     makespan of the expert plan (`opt_steps`, test.py:50-58); a scenario the planner cannot solve within
-    `time_limit` seconds is re-drawn, like the reference's `while actions is None: env.reset()` loop."""
+    `time_limit` seconds is re-drawn, like the reference's `while actions is None: env.reset()` loop.
+    Departure from the reference on maps larger than 64 x 64: the expert plans over a horizon of L * L steps instead of the
+    reference's config.max_steps = 256 (search.py:179), because a single shortest path there can be longer than 256 steps and the
+    reference's planner then raises; up to 64 x 64 the horizon is the reference's."""
     assert isinstance(agent_range, int) and isinstance(map_range, int), "fixed sizes only (the shipped fixtures' case)"
     path = path or "./test{}_{}.pkl".format(agent_range, map_range)
     maps, agents, goals, _ = generate_scenarios(test_num, map_range, agent_range, density, seed)
     extra = None
     if with_opt_steps:
-        from .search import plan
+        from .search import MAX_STEPS, plan
 
+        # the expert's time horizon: the reference's 256 steps (search.py:179) up to 64 x 64; on larger maps a shortest path alone can
+        # be longer than that at rho up to 0.5, so the horizon there is the cell count
+        horizon = MAX_STEPS if map_range <= 64 else map_range * map_range
         opt = []
         redraw_seed = seed * 100003
         for k in range(test_num):
-            res = plan(maps[k], agents[k], goals[k], time_limit)
+            res = plan(maps[k], agents[k], goals[k], time_limit, horizon)
             while res is None:
                 redraw_seed += 1
                 m1, a1, g1, _ = generate_scenarios(1, map_range, agent_range, density, redraw_seed)
                 maps[k], agents[k], goals[k] = m1[0], a1[0], g1[0]
-                res = plan(maps[k], agents[k], goals[k], time_limit)
+                res = plan(maps[k], agents[k], goals[k], time_limit, horizon)
             opt.append(len(res[0]))
         extra = {"opt_steps": opt, "opt_mean_steps": sum(opt) / len(opt)}  # test.py:58,76
     return save_tests(path, list(maps.astype(np.float32)), list(agents), list(goals), extra)
